@@ -2,7 +2,12 @@
 """Benchmark of the hot path on MI355X.  Default = BASELINE.json's headline metric: Mpixels/s of
 rasterize+interpolate forward+backward at 512^2, batch 64 per GPU (SURVEY.md 8(d) workload "CH").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ch|c2|c3|c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ch|c2|c3|c4] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if `--dump-outputs` is given and prints
+the line: the headline figure and nothing else.  `--full` adds everything else described below (per-kernel times and
+roofline, parity, CPU baselines, the literal step, the other configs and regimes, the N > 1 comparison legs, timing
+windows, the detail file); each of those takes runs of its own.
 
 `--gpus N` with N > 1 and no launcher environment re-executes this script under `python -m torch.distributed.run`
 with N ranks (one process per GPU, RCCL over xGMI); under a launcher (RANK / WORLD_SIZE set) it joins that job.
@@ -26,12 +31,20 @@ With N > 1 the step also contains the path's two exchanges (north_star; SURVEY 8
 output images to every rank -- issued per chunk of items on RCCL's stream while the next chunk is being rendered
 (`--chunks`, `--no-gather-images`) -- and the all-reduce of the gradient of the SHARED vertex attributes.
 
-Timing: after W warm-up steps, `--windows` (default 5) windows of EXACTLY K steps each, every window bracketed by
-barrier + synchronize on both sides and timed with the host clock (max over ranks) and with a hipEvent pair;
-`ms_per_step` is the MEDIAN window, `ms_per_step_min/max` the spread (median over event pairs).
+Timing: after W warm-up steps (in a single process continued until the warm-up has lasted WARMUP_MIN_S, so that the
+timed steps see the steady state), `--windows` windows of EXACTLY K steps each (default 1: the K steps are all that is
+timed; 5 with `--full`), every window bracketed by barrier + synchronize on both sides and timed with the host clock
+(max over ranks) and with a hipEvent pair; `ms_per_step` is the MEDIAN window, `ms_per_step_min/max` the spread
+(median over event pairs).
 
-Rank 0 prints ONE JSON line -- a COMPACT record, under 8 KB (the driver keeps 8 KB of stdout) -- and writes the complete
-record, everything described below with all its prose, to `bench_detail.json` next to this file (the line names it).  Short
+`--dump-outputs DIR`: right after the timed steps, what the last of them handed its caller -- the output image, rast, the
+gradients of pos and of the shared inputs (attr, or uv and the texture) -- goes to DIR/<name>.npy as float32.  An array of
+more than DUMP_SAMPLE values is written as a fixed sample of them (flat positions drawn from a generator seeded with
+DUMP_SEED, sorted), so two builds run with the same arguments can be compared output for output (the inputs are seeded).
+
+Rank 0 prints ONE JSON line -- a COMPACT record, under 8 KB (the driver keeps 8 KB of stdout) -- and with `--full` writes the
+complete record, everything described below with all its prose, to `bench_detail.json` next to this file, or wherever
+`--detail` names, in any run (the line names it).  With `--full`, short
 keys of the line: kernels {name: [avg ms per launch, alg frac, req frac]}; configs.<name> {ms, gpix, cov, k {kernel: ms},
 dom [longest kernel, alg frac, req frac], path [alg frac, req frac], par {...}}.  Beside the headline number it carries
   roofline      the LONGEST kernel of the step (hipEvents recorded by the library on the launch stream):
@@ -49,7 +62,8 @@ dom [longest kernel, alg frac, req frac], path [alg frac, req frac], par {...}}.
                 of oracle/refshim (one thread), when oracle/_ref is present;
   parity        id mismatches / max-abs errors of this very workload against the reference itself (oracle/_ref) when
                 present, else against the oracle;
-  configs       (default single-GPU run only) BASELINE configs[1], [2] and the [4] stand-in measured in the same process:
+  configs       (`--full` single-GPU run of the default workload only) BASELINE configs[1] to [3], the [4] stand-in and
+                the regimes above measured in the same process:
                 per config ms_per_step (median of windows), per-kernel times, roofline of its longest kernel and a parity
                 block of that very workload at its full resolution (`--no-extra-configs` leaves them out).
 `--dry-run-cpu` replaces the kernels by a stand-in and RCCL by gloo so that the launch / collective / timing
@@ -74,6 +88,11 @@ XGMI_LINK_GBS = 153.0          # per direction per link; 7 links per GPU, fully 
 HOST_MS_PER_CHUNK = 0.07       # measured host cost of issuing one chunk's six launches eagerly (compiled host layer: DESIGN 5; 0.20 through round 5)
 COPY_GBS = 5400.0              # streaming copy rate of one MI355X (tools/write_bw.py: read + write), prices the image-packing pass
 TRIANGLES = 10000
+WARMUP_MIN_S = 1.0             # single process: the warm-up goes on past W steps until it has lasted this long (the step time
+#                                still falls over the first hundred steps or more after set-up: 0.353 -> 0.319 ms in five
+#                                windows of 20 headline steps); the timed steps then measure the steady state
+DUMP_SAMPLE = 1 << 21          # --dump-outputs: values kept of one array (8 MB as float32; at most five arrays per workload)
+DUMP_SEED = 20240
 
 WORKLOADS = {
     "ch": dict(per_gpu=64, total=None, res=512, graph="ri", scaling="weak", attrs=4,
@@ -339,6 +358,8 @@ class Job:
             self.topo = dr.antialias_construct_topology_hash(self.tri) if self.full else None
         self.set_chunks(chunks)
         self.last_rast = None
+        self.keep_outputs = False    # --dump-outputs: every step keeps what it hands its caller until the next step starts
+        self.kept = None
 
     def set_gather_mode(self, fmt, pipelined):
         """What the image all-gather carries and when its result is waited for (nvdiffrast_amd/parallel.py ImageGather)."""
@@ -379,6 +400,8 @@ class Job:
             self.tex.grad = None
         self.last_rast = None             # (kept for coverage() after the LAST step only: a training loop does not hold the previous step's rast
         #                                   while it renders the next; holding it cost 17 us per headline step, profiles/r05q_keep_rast_ab.log)
+        self.kept = None
+        kept = [] if self.keep_outputs else None
         # gather_every = k: the consumer of the complete batch of images (a logger, a discriminator on another rank ...) wants
         # it every k-th step only; that step's all-gather then has k steps' worth of kernels to hide behind -- it is waited for
         # when its receive buffers are needed again, k steps later (or at the end of the timed window)
@@ -406,6 +429,9 @@ class Job:
             else:
                 torch.autograd.backward(out, self.G if self.chunks == 1 else self.G[a:b])
             self.last_rast = rast
+            if kept is not None:
+                kept.append((out.detach(), rast))
+        self.kept = kept
         if self.distributed:
             allreduce_shared_grads([self.shared] + ([self.tex] if self.full else []))
         if gather_now and self.pipe is not None:
@@ -436,8 +462,15 @@ class Job:
     def timed_windows(self, run, warmup, steps, windows):
         """`windows` windows of exactly `steps` steps, each bracketed by barrier + synchronize on both sides.
         Returns (host seconds per window, MAX over ranks; hipEvent milliseconds per window of this rank)."""
+        t0 = time.perf_counter()
         for _ in range(warmup):
             run()
+        if not self.dry and not self.distributed:              # (ranks would each decide on their own clock: W steps only)
+            self.fence()
+            while time.perf_counter() - t0 < WARMUP_MIN_S:
+                for _ in range(max(1, warmup)):
+                    run()
+                self.fence()
         host, evt = [], []
         for _ in range(windows):
             self.fence()
@@ -459,6 +492,20 @@ class Job:
             host.append(el)
             evt.append(float(e0.elapsed_time(e1)) if not self.dry else el * 1e3)
         return host, evt
+
+    def outputs(self):
+        """{name: tensor}: what the last step handed its caller (keep_outputs set): the output image and rast of the rank's items,
+        the gradients of pos and of the shared inputs."""
+        cat = lambda ts: ts[0] if len(ts) == 1 else torch.cat(ts)                                        # noqa: E731
+        res = {"image": cat([o for o, _ in self.kept])}
+        rasts = [r for _, r in self.kept if r is not None]
+        if rasts:
+            res["rast"] = cat(rasts)
+        res["pos_grad"] = self.pos.grad
+        res["uv_grad" if self.full else "attr_grad"] = self.shared.grad
+        if self.full:
+            res["tex_grad"] = self.tex.grad
+        return res
 
     # ---- everything below runs on rank 0 after the timed region -----------------------------------------------------
 
@@ -706,6 +753,20 @@ def window_stats(host_s, evt_ms, steps):
                           "on the launch stream around the same steps"}
 
 
+def dump_outputs(job, out_dir):
+    """--dump-outputs: job.outputs() as out_dir/<name>.npy in float32, an array of more than DUMP_SAMPLE values as the sample
+    of it at sorted flat positions drawn from a generator seeded with DUMP_SEED (the same positions for the same shape)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in job.outputs().items():
+        if t is None:
+            continue
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, t.numel(), DUMP_SAMPLE))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+
+
 def graph_replay_in_child(argv, keys, script=None):
     """The same step replayed from ONE hipGraph (nothing on the path allocates at the C-ABI level or synchronises the host, so
     the whole step captures): what the kernels alone take when the host's launch work is out of the way.  Measured by a child
@@ -773,7 +834,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--windows", type=int, default=5, help="timing windows of --steps steps each; the median window is reported")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="timing windows of --steps steps each; the median window is reported (default 1, with --full 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: per-kernel times and roofline, parity, "
+                         "CPU baselines, the literal step, the other configs and regimes, the N > 1 comparison legs, the detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; large arrays as a fixed seeded sample)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="ch")
     ap.add_argument("--batch", type=int, default=None, help="items per GPU (overrides the workload's)")
     ap.add_argument("--res", type=int, default=None, help="resolution (overrides the workload's; dry runs use a small one)")
@@ -791,7 +858,7 @@ def main():
                     help="N > 1: wait for a step's images inside that step (default: collect them at the end of the NEXT step, so the "
                          "link time hides behind its kernels)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-configs", action="store_true", help="default run: do not also measure BASELINE configs[1], [2], [4]")
+    ap.add_argument("--no-extra-configs", action="store_true", help="--full: do not also measure the other BASELINE configs and the regimes")
     ap.add_argument("--cpu-items", type=int, default=64, help="items in the CPU-oracle sample")
     ap.add_argument("--graph", action="store_true",
                     help="capture the step into one hipGraph and time replays (single GPU only; the default, and the "
@@ -802,6 +869,8 @@ def main():
     ap.add_argument("--detail", default=None, help="where the complete record goes (default: bench_detail.json next to this file)")
     ap.add_argument("--dry-run-cpu", action="store_true", help="gloo + stand-in kernels: exercises the multi-rank plumbing without GPUs")
     args = ap.parse_args()
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
 
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     if args.gpus > 1 and not launched:
@@ -872,6 +941,7 @@ def main():
 
     job = Job(args.workload, N, total_items, first, rank, world, dev, dry, RES, distributed, chunks, gather, args.gather_every,
               gather_format=args.gather_format if gather else "f32", gather_pipelined=pipelined)
+    job.keep_outputs = bool(args.dump_outputs)
 
     run = job.step
     if args.graph:
@@ -890,6 +960,9 @@ def main():
 
     host, evt = job.timed_windows(run, args.warmup, args.steps, max(1, args.windows))
     ms_per_step, timing = window_stats(host, evt, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(job, args.dump_outputs)
+    job.keep_outputs, job.kept = False, None
     ranks_seen = world
     if distributed:
         ones = torch.ones(1, dtype=torch.float64, device=dev)
@@ -897,13 +970,13 @@ def main():
         ranks_seen = int(round(float(ones.item())))
         assert ranks_seen == dist.get_world_size()
     # The image all-gather is pure xGMI traffic whose size does not depend on how fast the kernels are: report the
-    # same job without it next to `value`, and the link arithmetic, so that the two effects can be told apart.
+    # same job without it next to `value` (--full), and the link arithmetic, so that the two effects can be told apart.
     collective = None
     if distributed:
         from nvdiffrast_amd.parallel import payload_bytes_per_pixel, payload_channels
-        ms_ng = ms_per_step
+        ms_ng = None if gather else ms_per_step
         ms_f32 = None
-        if gather:
+        if gather and args.full:
             planned = job.chunks
             job.drain()
             job.gather_on = False
@@ -936,12 +1009,12 @@ def main():
             "xgmi_links_per_gpu_used": links, "xgmi_link_gbs": XGMI_LINK_GBS,
             # every link carries one rank's images, all links in parallel: the floor does not shrink with more GPUs
             "xgmi_floor_ms": round(img_bytes / (XGMI_LINK_GBS * 1e9) * 1e3, 4) if links else None,
-            "ms_per_step_without_image_gather": round(ms_ng, 4),
-            "value_without_image_gather": round(total_items * RES * RES / (ms_ng * 1e-3) / 1e6, 1),
+            "ms_per_step_without_image_gather": None if ms_ng is None else round(ms_ng, 4),
+            "value_without_image_gather": None if ms_ng is None else round(total_items * RES * RES / (ms_ng * 1e-3) / 1e6, 1),
             "chunks": job.chunks, "chunk_plan": chunk_plan, "gather_every": job.gather_every,
             # the curve the link arithmetic predicts, from THIS run's compute time per item (gather-free step / items)
-            "predicted_scaling": predicted_scaling(ms_ng / max(N, 1), wl["scaling"], wl["per_gpu"] or N, wl["total"] or total_items, item_bytes,
-                                                   channels=C_out),
+            "predicted_scaling": None if ms_ng is None else predicted_scaling(ms_ng / max(N, 1), wl["scaling"], wl["per_gpu"] or N,
+                                                                              wl["total"] or total_items, item_bytes, channels=C_out),
         }
 
     P_total = total_items * RES * RES
@@ -952,7 +1025,7 @@ def main():
         kernels = roofline = parity = cpu = cpu_ref = configs = literal = None
         path_frac = {"alg": None, "required": None, "counter": None}
         coverage = tile_cov = None
-        if not dry:
+        if not dry and args.full:
             coverage, tile_cov = job.coverage(), job.tile_coverage()
             kernels, roofline, path_frac = job.profile_kernels(max(3, min(args.steps, 10)), ms_per_step)
             if world == 1:
@@ -986,8 +1059,8 @@ def main():
                "chunks": job.chunks, "gather_images": bool(gather), "gather_every": job.gather_every,
                "gather_format": job.gather_format if gather else None, "gather_pipelined": job.pipe is not None,
                "launch": "hipGraph replay" if args.graph else "eager"}
-        # ---- the other BASELINE configs and the regimes the benchmark scene hides: same process, single GPU, default run only ---
-        if (not dry and world == 1 and not distributed and args.workload == "ch" and args.batch is None and args.res is None
+        # ---- the other BASELINE configs and the regimes the benchmark scene hides: same process, single GPU, default workload, --full
+        if (args.full and not dry and world == 1 and not distributed and args.workload == "ch" and args.batch is None and args.res is None
                 and not args.graph and not args.no_extra_configs):
             del job
             torch.cuda.empty_cache()
@@ -1035,8 +1108,8 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        # (a CPU dry run -- the test suite's -- leaves no record next to this file unless asked for one with --detail)
-        detail = args.detail or (None if args.dry_run_cpu else os.path.join(ROOT, "bench_detail.json"))
+        # (a plain run, and a CPU dry run -- the test suite's -- leave no record next to this file unless asked for one with --detail)
+        detail = args.detail or (os.path.join(ROOT, "bench_detail.json") if args.full and not args.dry_run_cpu else None)
         if detail:
             try:
                 with open(detail, "w") as f:

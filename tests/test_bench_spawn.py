@@ -31,6 +31,24 @@ def test_single_rank_line():
     assert j["config"]["gather_images"] is False and j["config"]["chunks"] == 1
 
 
+def test_plain_run_times_the_steps_once_and_dumps_the_last_step(tmp_path):
+    """A plain run times one window of exactly --steps steps; --dump-outputs writes what the last of them handed its caller
+    (float32), the same in a second run with the same arguments."""
+    import numpy as np
+    runs = []
+    for d in ("a", "b"):
+        j = _run("--batch", "4", "--steps", "3", "--dump-outputs", str(tmp_path / d))
+        assert j["steps"] == 3 and j["timing"]["windows"] == 1 and j["ms_per_step"] > 0 and j["detail"] is None
+        assert j["kernels"] is None and j["configs"] is None and j["collective"] is None
+        runs.append({f: np.load(str(tmp_path / d / f)) for f in sorted(os.listdir(str(tmp_path / d)))})
+    a, b = runs
+    assert set(a) == {"image.npy", "pos_grad.npy", "attr_grad.npy"} == set(b)          # (the stand-in renders no rast)
+    assert a["image.npy"].shape == (4, 32, 32, 4) and a["pos_grad.npy"].shape[0] == 4 and a["attr_grad.npy"].shape[0] == 1
+    for k, v in a.items():
+        assert v.dtype == np.float32 and np.isfinite(v).all() and np.array_equal(v, b[k]), k
+    assert np.abs(a["attr_grad.npy"]).max() > 0
+
+
 @pytest.mark.parametrize("workload,scaling,total", [("ch", "weak", 8), ("c4", "strong", 256)])
 def test_two_ranks_are_spawned_and_take_part(workload, scaling, total):
     flags = ["--gpus", "2", "--chunks", "4", "--workload", workload] + (["--batch", "4"] if workload == "ch" else [])
@@ -46,7 +64,7 @@ def test_two_ranks_are_spawned_and_take_part(workload, scaling, total):
 def test_two_ranks_default_is_the_packed_pipelined_gather_with_the_other_figures_beside_it():
     """The default N > 1 line: the output images all-gathered EVERY step as rgb8 (three channels, one byte each), collected one
     step later; next to it the same job without the gather and with the f32 gather inside the step (rounds 2-5's default)."""
-    j = _run("--gpus", "2", "--batch", "4")
+    j = _run("--gpus", "2", "--batch", "4", "--full")
     c = j["collective"]
     assert j["config"]["gather_format"] == "rgb8" and j["config"]["gather_pipelined"] is True and j["config"]["chunks"] == 1
     assert c["gather_format"] == "rgb8" and c["gather_pipelined"] is True and c["gather_payload"].startswith("3 of 4 channels, 1 byte")
@@ -102,7 +120,7 @@ def test_chunk_policy_follows_the_link_arithmetic():
 
 def test_default_chunking_in_a_spawned_job():
     assert _run("--gpus", "2", "--batch", "4")["config"]["chunks"] == 1               # dry-run items are tiny: one chunk
-    j = _run("--gpus", "2", "--workload", "c4")
+    j = _run("--gpus", "2", "--workload", "c4", "--full")
     assert j["collective"]["chunk_plan"]["predicted_step_ms_by_chunks"] and j["collective"]["predicted_scaling"]["with_image_gather"]["8"] > 0
 
 
@@ -121,7 +139,7 @@ def test_eight_ranks_c4():
 def test_gather_every_kth_step_at_world_8():
     """the one schedule with an image gather that the link arithmetic lets scale: the complete batch of
     images every k-th step only, its all-gather running behind the following steps' kernels (double-buffered receive)."""
-    j = _run("--gpus", "8", "--workload", "c4", "--windows", "2", "--gather-every", "4", "--steps", "5")
+    j = _run("--gpus", "8", "--workload", "c4", "--windows", "2", "--gather-every", "4", "--steps", "5", "--full")
     assert j["n_gpus"] == 8 and j["rccl_ranks"] == 8 and j["config"]["gather_every"] == 4 and j["config"]["gather_images"] is True
     assert j["gathered_rows_total"] == 256                                   # the gathered batch is complete when it is there
     assert set(j["collective"]["predicted_scaling"]) >= {"with_image_gather", "without_image_gather", "gather_every_4", "gather_every_8"}

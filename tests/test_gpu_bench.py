@@ -1,4 +1,4 @@
-"""bench.py on the GPU: the default line's contract, and the N > 1 code path (RCCL process group, broadcast of the shared
+"""bench.py on the GPU: the plain line and its output dump, the --full line's contract, and the N > 1 code path (RCCL process group, broadcast of the shared
 geometry, chunked image all-gather overlapped with rendering, shared-gradient all-reduce) run with a group of one --
 the only way to execute those RCCL calls on a 1-GPU box."""
 import json
@@ -7,16 +7,18 @@ import subprocess
 import sys
 
 import pytest
+from conftest import grad_tol
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(*flags, line=False):
-    """Runs bench.py; returns the COMPLETE record (bench.py --detail), or with line=True (the stdout line, the record)."""
+def _bench(*flags, line=False, full=True):
+    """Runs bench.py (with --full unless full=False); returns the COMPLETE record (bench.py --detail), or with line=True
+    (the stdout line, the record)."""
     import tempfile
     detail = os.path.join(tempfile.mkdtemp(), "detail.json")
-    flags = tuple(flags) + ("--detail", detail)
+    flags = tuple(flags) + ("--detail", detail) + (("--full",) if full else ())
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
@@ -30,6 +32,45 @@ def _bench(*flags, line=False):
     assert len(lines[0]) < 8000, len(lines[0])              # the driver keeps 8 KB of stdout
     full = json.load(open(detail))
     return (json.loads(lines[0]), full) if line else full
+
+
+def _dumped(d):
+    import numpy as np
+    return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+
+def test_plain_line_and_output_dump():
+    """A plain run: the headline figure only (one window of exactly --steps steps, nothing measured beside it, no detail file
+    unless asked for), and --dump-outputs: the last timed step's image, rast and gradients as float32; a second run with the
+    same arguments gives the same image and rast, and the same gradients to the single-op bar (they are sums in atomic order)."""
+    import tempfile
+    import numpy as np
+    dirs = [tempfile.mkdtemp(), tempfile.mkdtemp()]
+    runs = [_bench("--batch", "8", "--dump-outputs", d, line=True, full=False) for d in dirs]
+    ln, j = runs[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert k in ln and ln[k] == j[k], k
+    assert ln["value"] > 0 and ln["ms_per_step"] > 0 and ln["higher_is_better"] is True and ln["dtype"] == "f32"
+    assert j["steps"] == 3 and j["warmup"] == 2 and j["timing"]["windows"] == 1 and j["timing"]["steps_per_window"] == 3
+    for k in ("kernels", "roofline", "parity", "cpu_baseline", "literal_step", "configs"):
+        assert j[k] is None, k
+    a, b = _dumped(dirs[0]), _dumped(dirs[1])
+    assert set(a) == {"image", "rast", "pos_grad", "attr_grad"} == set(b)
+    assert sum(os.path.getsize(os.path.join(dirs[0], f)) for f in os.listdir(dirs[0])) <= 64 << 20
+    assert a["pos_grad"].shape == (8, 5151, 4) and a["attr_grad"].shape == (1, 5151, 4)
+    for k, v in a.items():
+        assert v.dtype == np.float32 and np.isfinite(v).all(), k
+    assert np.array_equal(a["image"], b["image"]) and np.array_equal(a["rast"], b["rast"])
+    for k in ("pos_grad", "attr_grad"):
+        assert np.abs(a[k] - b[k]).max() <= grad_tol(a[k]), k
+    sys.path.insert(0, ROOT)
+    import bench
+    n = 8 * 512 * 512 * 4                                         # image and rast: more than DUMP_SAMPLE values, written as the sample
+    pos = np.unique(np.random.default_rng(bench.DUMP_SEED).integers(0, n, bench.DUMP_SAMPLE))
+    assert a["image"].shape == a["rast"].shape == pos.shape
+    ids = a["rast"][pos % 4 == 3]                                 # rast's fourth channel: triangle id + 1 (0 = background)
+    assert (ids == np.round(ids)).all() and (ids >= 0).all() and (ids > 0).any() and ids.max() <= 10000
+    assert np.abs(a["attr_grad"]).max() > 0 and np.abs(a["pos_grad"]).max() > 0
 
 
 def test_default_line_contract():
