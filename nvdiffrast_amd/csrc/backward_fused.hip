@@ -19,6 +19,7 @@
 // (dy[4], b0, b1 and nine position-gradient components... per row) fit 8 waves/SIMD only with two rows per wave.
 #include "nvdr_device.hpp"
 #include "nvdr_host.hpp"
+#include "nvdr_plan.hpp"
 #include "nvdr_raster_tape.hpp"
 
 namespace nvdr {
@@ -327,9 +328,6 @@ __global__ __launch_bounds__(kFuThreads, ENABLE_DA ? 6 : 8) void k_interp_raster
 
 using namespace nvdr;
 
-// LDS of one workgroup for `slots` table entries of A + 3 components: sums, key, used-list entry, header.
-static size_t fused_lds_bytes(int slots, int A) { return (size_t)slots * (8 * (size_t)(A + 3) + 6) + 16; }
-
 extern "C" int nvdr_interpolate_rasterize_grad(const float* attr, const float* rast, const int32_t* tri, const float* pos,
                                                const float* dy, int attr_instance, int attr_n, int pos_instance,
                                                int N, int V, int A, int T, int H, int W,
@@ -380,12 +378,9 @@ extern "C" int nvdr_interpolate_rasterize_grad(const float* attr, const float* r
     const long long total = p.flags.order ? tile_flags_ordered_grid(p.flags, (64 / kFuBlockW) * (64 / kFuBlockH)) : (long long)gx * gy * N;
     NVDR_REQUIRE(total < (1ll << 30), "interpolate_rasterize_grad: too many pixel blocks");
     dim3 grid((unsigned)(((total + 7) / 8) * 8)), block(kFuThreads);
-    // LDS vertex table: as many power-of-two slots as fit in 32 KiB (four 8-wave workgroups per CU), at most 512;
-    // none (plain atomics) for vertices too wide for even 32 slots in 64 KiB
-    int slots = 512;
-    while (slots > 32 && fused_lds_bytes(slots, A) > 32 * 1024) slots >>= 1;
-    if (fused_lds_bytes(slots, A) > 64 * 1024) slots = 0;
-    const size_t lds = fused_lds_bytes(slots, A);
+    // LDS vertex table (nvdr_plan.hpp): up to 512 slots in 32 KiB, at least 32 in 64 KiB, else none (plain atomics)
+    const int slots = nvdr_plan::fused_grad_slots(A);
+    const size_t lds = nvdr_plan::fused_grad_lds(slots, A);
     const bool vec4 = (A == 4) && !((uintptr_t)attr & 15) && !((uintptr_t)dy & 15);
     const bool vec2 = (A == 2) && !((uintptr_t)attr & 7) && !((uintptr_t)dy & 7);
     {

@@ -10,6 +10,7 @@
 //                 (vertex, attribute) per block.
 #include "nvdr_device.hpp"
 #include "nvdr_host.hpp"
+#include "nvdr_plan.hpp"
 #include <type_traits>
 
 namespace nvdr {
@@ -578,13 +579,11 @@ extern "C" int nvdr_interpolate_grad(const float* attr, const float* rast, const
     const long long total = p.flags.order ? tile_flags_ordered_grid(p.flags, (64 / kIpBlockW) * (64 / kIpBlockH)) : (long long)gx * gy * N;   // (nvdr_device.hpp TileFlags)
     NVDR_REQUIRE(total < (1ll << 30), "interpolate_grad: too many pixel blocks");
     dim3 grid((unsigned)(((total + 7) / 8) * 8)), block(kIpThreads);
-    // LDS vertex table: as many power-of-two slots as fit in 20 KiB (8 workgroups per CU), at most 512.
-    int slots = 512;
-    while (slots > 32 && (size_t)slots * (8 * A + 6) + 16 > 20 * 1024) slots >>= 1;
-    // Vertices too wide for even the smallest table (A >= 256) go without one: every contribution becomes a
-    // hardware f32 atomic, as in the reference (interpolate.cu:198-210), instead of an error.
-    if ((size_t)slots * (8 * A + 6) + 16 > 64 * 1024) slots = 0;
-    const size_t lds = (size_t)slots * (8 * A + 6) + 16;    // sums + key + used-list entry per slot
+    // LDS vertex table (nvdr_plan.hpp): up to 512 slots in 20 KiB, at least 32.  Vertices too wide for even the smallest table
+    // (A >= 256) go without one: every contribution becomes a hardware f32 atomic, as in the reference (interpolate.cu:198-210),
+    // instead of an error.
+    const int slots = nvdr_plan::interp_grad_slots(A);
+    const size_t lds = nvdr_plan::interp_grad_lds(slots, A);
     const bool vec4 = (A == 4) && !((uintptr_t)attr & 15) && !((uintptr_t)dy & 15);
     const bool vec2 = (A == 2) && !((uintptr_t)attr & 7) && !((uintptr_t)dy & 7);
     {

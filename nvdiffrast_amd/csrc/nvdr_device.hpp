@@ -324,6 +324,19 @@ __device__ __forceinline__ void block_max_update(uint32_t* s_max, float m) {
     if (lane_id() == 63) atomicMax(s_max, (uint32_t)__float_as_int(mm));
 }
 
+// block_max_update, and the largest wave SUM of `m` into *s_sum (for the bound of FixedScale32's cells): one DPP sum per wave
+// and one LDS max per wave, order independent (the scale must not depend on which wave finishes first).
+__device__ __forceinline__ void block_max_sum_update(uint32_t* s_max, uint32_t* s_sum, float m) {
+    if (__ballot(m != 0.f) == 0) return;                            // NaN != 0 is true
+    const uint32_t bits = (uint32_t)__float_as_int(m) & 0x7FFFFFFFu;
+    const float mm = wave_max_to_last(__int_as_float((int)min(bits, 0x7F800000u)));
+    const float ss = wave_sum_to_last(m);                           // NaN / inf stay visible
+    if (lane_id() == 63) {
+        atomicMax(s_max, (uint32_t)__float_as_int(mm));
+        atomicMax(s_sum, (uint32_t)__float_as_int(ss) & 0x7FFFFFFFu);
+    }
+}
+
 // A magnitude as BITS: for non-negative floats unsigned order is float order, and inf / NaN patterns sort above every finite one, so
 // max(m, mag_bits(a)) keeps a NaN visible like max_abs_keep_nan below -- with one v_and and one v_max_u32 instead of a compare, a
 // select, an fmax and an fabs.  The backward kernels run at 95 % of their vector issue rate: instructions are their time.
@@ -354,16 +367,21 @@ struct FixedScale {
 };
 
 // 32-bit variant for accumulators with few terms per cell (texel patches): x -> round(x * 2^s) with
-// s = 20 - e (M < 2^(e+1) the largest summand), so one summand stays below 2^21, a pre-summed run of 16
-// below 2^25 and a cell holding <= 512 summands below 2^30.  Resolution 2^-21 of M (rounding error
-// <= 2^-22 M per summand: the ulp scale of an f32 sum of that size).
+// s = 29 - e, where B < 2^(e+1) bounds the magnitude of every summand and of every cell's total, so a
+// cell stays below 2^30 plus its roundings (<= 1024 summands of <= 1/2 each): far from 2^31.  The
+// texture gradient takes B = 4 x the largest of its four waves' sums of max_c |dy| over their pixels
+// (block_max_sum_update): a texel's total over the block is at most sum_p max_c |dy_p| (the bilinear
+// weights of one pixel and level sum to 1).  Resolution 2^-30 B, at most 2^-22 of the block's largest
+// |dy| M and far finer where one outlier sets M.  (Scaling by M alone, 2^-21 M, let the roundings of a
+// few hundred small summands per texel of a magnified texture add up to 1.9x the gradient bar when an
+// outlier set M: tests/test_gpu_texture_grad_precision.py, tests/test_texgrad_precision_model.py.)
 struct FixedScale32 {
     float scale, inv;
-    __device__ __forceinline__ explicit FixedScale32(uint32_t max_bits) {
-        int e = (int)(max_bits >> 23) - 127;                       // M < 2^(e+1)
-        e = max(e, -100);                                            // keep 2^(20-e) finite for denormal maxima
-        scale = __int_as_float((127 + 20 - e) << 23);
-        inv   = __int_as_float((127 - 20 + e) << 23);
+    __device__ __forceinline__ explicit FixedScale32(uint32_t bound_bits) {
+        int e = (int)(bound_bits >> 23) - 127;                     // B < 2^(e+1)
+        e = max(e, -97);                                             // keep 2^(29-e) finite for denormal bounds
+        scale = __int_as_float((127 + 29 - e) << 23);
+        inv   = __int_as_float((127 - 29 + e) << 23);
     }
     __device__ __forceinline__ int to_fixed(float x) const { return __float2int_rn(x * scale); }
     __device__ __forceinline__ float to_float(int t) const { return (float)t * inv; }

@@ -18,6 +18,7 @@
 //                block are accessed as float4 vectors when the channel count allows (k_mip_grad_vec).
 #include "nvdr_device.hpp"
 #include "nvdr_host.hpp"
+#include "nvdr_plan.hpp"
 
 namespace nvdr {
 
@@ -669,13 +670,13 @@ __global__ __launch_bounds__(256) void k_tex_fwd_cube(const TexParams p)
 // Texel-gradient accumulator of one workgroup: an LDS open-addressing table of 8x2-texel patches
 // keyed by (level, patch x, patch y), each patch holding 16 texels x C channels of 32-bit fixed-point
 // sums (nvdr_device.hpp: LDS integer atomics are ~30x cheaper than ds_add_f32, and a global atomic
-// costs one memory transaction per touched cache line).  32 bits (resolution 2^-22 of the block's
-// largest |dy|, i.e. the ulp of an f32 sum of that size) instead of the vertex tables' 64 keep the
-// table at 25 KB so that six workgroups fit a CU.  Every tap of the workgroup's 16x16 pixels is
+// costs one memory transaction per touched cache line).  32 bits (scaled to a bound of every texel's
+// total over the block, nvdr_device.hpp FixedScale32) instead of the vertex tables' 64 keep the table
+// at 25 KB so that six workgroups fit a CU.  Every tap of the workgroup's 16x16 pixels is
 // added here; at the end each patch row is flushed by consecutive lanes, so one atomic instruction
 // covers a few whole lines instead of 64 scattered ones, and pixels that hit the same texel (e.g. a
 // constant-uv background) cost one global atomic per workgroup instead of one per pixel.
-// The fixed-point scale comes from the block's largest |dy| (every tap weight is in [0,1]).
+// The fixed-point scale comes from the block's sum of max_c |dy| (every tap weight is in [0,1]).
 struct PatchTable {
     uint32_t* keys;               // [groups]  0 = empty
     int* vals;                    // [groups * 16 * C] 32-bit fixed-point sums
@@ -713,15 +714,15 @@ __global__ __launch_bounds__(256, 5) void k_tex_grad(const TexParams p, int grou
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_mem[];
     const int C = C_CT > 0 ? C_CT : p.channels;          // compile-time channel count for the common cases: the loops unroll
-    // LDS layout: vals [groups*16*C] | keys [groups] | {block max, used count, -, -} | used-patch list [groups]
+    // LDS layout: vals [groups*16*C] | keys [groups] | {block max, used count, largest wave sum, -} | used-patch list [groups]
     PatchTable tab{(uint32_t*)((int*)s_mem + (size_t)groups * 16 * C), (int*)s_mem, groups, C};
-    uint32_t* s_max = tab.keys + groups;                                    // [0] block max, [1] number of used patches
+    uint32_t* s_max = tab.keys + groups;                                    // [0] block max, [1] number of used patches, [2] wave sum
     int* s_used = (int*)(s_max + 4);                                        // [groups] indices of the used patches (flush)
     int px = 0, py = 0, pz = 0, blk = 0; bool inside;
     if (!tex_pixel(p, px, py, pz, inside, &blk)) return;
     if (p.heavy && !p.heavy[blk]) return;                        // two-kernel pass: blocks that k_tex_grad_light has finished
     if (groups > 0 && !(p.dbg & 2048)) tab.clear(threadIdx.x, 256);
-    if (threadIdx.x == 0) { s_max[0] = 0u; s_max[1] = 0u; }
+    if (threadIdx.x == 0) { s_max[0] = 0u; s_max[1] = 0u; s_max[2] = 0u; }
     __syncthreads();
 
     const int tz = (p.texDepth == 1) ? 0 : pz;
@@ -764,12 +765,13 @@ __global__ __launch_bounds__(256, 5) void k_tex_grad(const TexParams p, int grou
             }
         }
     }
-    block_max_update(s_max, m);
+    block_max_sum_update(s_max, s_max + 2, m);
     __syncthreads();
     const uint32_t maxBits = *s_max;
     if (maxBits == 0u) return;                                   // nobody has anything to scatter
-    const bool direct = (groups == 0) || maxBits >= 0x7F800000u; // no table / inf or NaN present: plain f32 atomics
-    const FixedScale32 fs(direct ? 0x3F800000u : maxBits);
+    const float bound = 4.f * __int_as_float((int)s_max[2]);    // >= any texel's total over the block (FixedScale32)
+    const bool direct = (groups == 0) || maxBits >= 0x7F800000u || !(bound < INFINITY);   // no table / inf or NaN: f32 atomics
+    const FixedScale32 fs(direct ? 0x3F800000u : (uint32_t)__float_as_int(bound));
 
     // One tap's contribution goes to the LDS table when the tap has a slot; taps without one (table full, no
     // table, inf/NaN present) are sent to memory directly under a wave-uniform test, off the common path.
@@ -1108,7 +1110,7 @@ __global__ __launch_bounds__(256, 6) void k_tex_grad_lean(const TexParams p, int
 {
     constexpr bool kTri = (FILTER == TEX_LML);
     extern __shared__ __attribute__((aligned(16))) unsigned char s_mem[];
-    // LDS layout as in k_tex_grad: vals [groups*16*C] | keys [groups] | {block max, used count, -, -} | used-patch list [groups]
+    // LDS layout as in k_tex_grad: vals [groups*16*C] | keys [groups] | {block max, used count, largest wave sum, -} | used-patch list [groups]
     PatchTable tab{(uint32_t*)((int*)s_mem + (size_t)groups * 16 * C), (int*)s_mem, groups, C};
     uint32_t* s_max = tab.keys + groups;
     int* s_used = (int*)(s_max + 4);
@@ -1116,7 +1118,7 @@ __global__ __launch_bounds__(256, 6) void k_tex_grad_lean(const TexParams p, int
     if (!tex_pixel(p, px, py, pz, inside, &blk)) return;
     if (p.heavy && !p.heavy[blk]) return;                                    // finished by the light kernel
     tab.clear(threadIdx.x, 256);
-    if (threadIdx.x == 0) { s_max[0] = 0u; s_max[1] = 0u; }
+    if (threadIdx.x == 0) { s_max[0] = 0u; s_max[1] = 0u; s_max[2] = 0u; }
     const int lane = threadIdx.x & 63;
     const int tz = (p.texDepth == 1) ? 0 : pz;
     const size_t pidx = (size_t)px + (size_t)p.imgW * (py + (size_t)p.imgH * pz);
@@ -1153,14 +1155,15 @@ __global__ __launch_bounds__(256, 6) void k_tex_grad_lean(const TexParams p, int
         }
         if (!active) m = 0.f;
     }
-    block_max_update(s_max, m);
+    block_max_sum_update(s_max, s_max + 2, m);
     int level0 = 0, level1 = 0; float flevel = 0.f;
     if (kTri && active) tex_mip_level<FILTER, false, false>(p, pidx, level0, level1, flevel, nullptr, make_float3(0.f, 0.f, 0.f), nullptr, zt, &da);
     __syncthreads();
     const uint32_t maxBits = s_max[0];
     if (maxBits == 0u) return;                                   // nobody has anything to scatter
-    const bool direct = maxBits >= 0x7F800000u;                  // inf or NaN present: plain f32 atomics
-    const FixedScale32 fs(direct ? 0x3F800000u : maxBits);
+    const float bound = 4.f * __int_as_float((int)s_max[2]);    // >= any texel's total over the block (FixedScale32)
+    const bool direct = maxBits >= 0x7F800000u || !(bound < INFINITY);   // inf or NaN present: plain f32 atomics
+    const FixedScale32 fs(direct ? 0x3F800000u : (uint32_t)__float_as_int(bound));
 
     // ---- identical footprints inside the wave ------------------------------------------------------------------------------
     // dsc[c] = what this lane scatters for channel c: its own upstream gradient; the group's total for a group's first lane;
@@ -2222,13 +2225,11 @@ extern "C" int nvdr_texture_grad(const float* tex, const float* const* mip_ptrs_
     NVDR_REQUIRE(!(filter_mode == TEX_LML && p.bias) || g_mip_level_bias, "texture_grad: g_mip_level_bias missing");
     const dim3 grid = tex_grid(p);
     const bool bo = (filter_mode >= TEX_LMN) && !p.uvDA;
-    // LDS patch table: as many power-of-two patches of 16 texels as fit in 26 KiB (at most 512), so that
-    // six workgroups share a CU (the kernel is latency bound: occupancy matters more than table size);
-    // none (direct atomics) when even 16 patches do not fit.
-    int groups = 512;
-    while (groups >= 16 && (size_t)groups * (8 + 64 * (size_t)C) + 16 > 26 * 1024) groups >>= 1;
-    if (groups < 16 || tex_w > 32768 || (long long)tex_h * (cube ? 6 : 1) > 65536 || (debug_flags() & 256)) groups = 0;   // key format
-    const size_t lds = (size_t)groups * (8 + 64 * (size_t)C) + 16;         // 16 texels x C sums + key 4 B + used-list entry 4 B per patch
+    // LDS patch table (nvdr_plan.hpp): up to 512 patches of 16 texels in 26 KiB, so that six workgroups share a CU; none (direct
+    // atomics) when even 16 patches do not fit or the texture is beyond the key format.
+    int groups = nvdr_plan::tex_grad_groups(C, tex_w, tex_h, cube);
+    if (debug_flags() & 256) groups = 0;
+    const size_t lds = nvdr_plan::tex_grad_lds(groups, C);
     // Second reduction level for constant-uv regions (TexParams::rec), when the caller brought scratch and the kernel has
     // a uniform-wave path for this mode (2-D, bilinear footprint, level from uv_da) and a table to fall back on.
     const long long nrec = tex_grad_records(N, H, W);
